@@ -9,12 +9,18 @@ work of pipeline_FaithDiff_tlc.py:1324-1409.  Weights are seeded random-init of 
 params, built by the product factory FaithDiff_pipeline('random-init', ...)), inputs synthetic; everything is
 resident in HBM before timing.
 
+A plain run (``python bench.py --gpus 1 --steps N --warmup W``) does only what the headline figure needs: build the
+model, W warm-up steps, N timed steps, the result line.  Every other leg below (roofline / kernel-family graphs, VAE
+decode, the ``pipe(...)`` call, C3, the CPU baseline) runs only with ``--full``.  ``--dump-outputs DIR`` writes what the
+last timed step computed as DIR/<name>.npy (float32; inputs are seeded, so two builds can be compared output for
+output).
+
 Launch: ``python bench.py --gpus N`` starts N rank processes itself (torch.distributed.run, before any GPU call)
 unless it already runs under torchrun (WORLD_SIZE set, which must equal N).
 
 Workloads (``--workload``; all ranks time exactly --steps steps between barrier + synchronize, max over ranks):
   c2 (default)  every rank restores its own 1024^2 image (replicas, no data-path collective): value = total
-                steps/s, scaling "weak".  The same line also carries
+                steps/s, scaling "weak".  With ``--full`` the same line also carries
                   * "pipeline": the product ``pipe(...)`` call end to end at C2 (encode_prompt, denoise encoder,
                     VAE encode, 20 steps, VAE decode, postprocess) -- s/image and its per-step time;
                   * "c3": BASELINE configs[2] -- one 4096^2 image (49 TLC tiles, tiled VAE) restored by ALL
@@ -26,6 +32,7 @@ Workloads (``--workload``; all ranks time exactly --steps steps between barrier 
                 value = tile-steps/s of the whole job (strong scaling);
   c5            BASELINE configs[4]: 8 images of 1024^2 x 50 steps split over the ranks: value = images/s.
 
+With ``--full``:
 roofline: the dominant kernel family is the MFMA GEMM (gemm8_kernel + gemm_kernel: every projection, FF and
 implicit-GEMM conv of the UNet, ~80 % of a step).  While the UNet forward is captured, every launch is also
 recorded (ops.set_recorder); the GEMM launches of one forward are then captured on their own into a second
@@ -73,6 +80,10 @@ def parse(argv=None):
     ap.add_argument("--unet-fp16", action="store_true", help="UNet computing in fp16 (the reference's own UNet dtype, "
                                                              "create_FaithDiff_model.py:21-22) instead of bf16 "
                                                              "(BASELINE configs[1], the default)")
+    ap.add_argument("--full", action="store_true", help="also run the legs beside the headline figure: roofline / "
+                                                        "kernel-family graphs, VAE decode, pipe(...) call, C3, CPU "
+                                                        "baseline (each can be switched off with its --no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed to DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-vae", action="store_true")
     ap.add_argument("--no-pipeline", action="store_true", help="skip the C2 pipe(...) s/image leg")
@@ -209,6 +220,22 @@ class EventTimer:
         return ea.elapsed_time(eb)
 
 
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays, rank=0):
+    """--dump-outputs: every array as path/<name>.npy in float32 (ranks > 0: <name>_rank<r>.npy).  Together they stay
+    under DUMP_BUDGET_BYTES: an array over its share is written as a fixed seeded sample of its flattened elements."""
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_BUDGET_BYTES // max(1, len(arrays)) // 4
+    for name, t in arrays.items():
+        a = t.detach().to("cpu", torch.float32).contiguous().numpy()
+        if a.size > share:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, size=share, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, name + (f"_rank{rank}" if rank else "") + ".npy"), a)
+
+
 # ------------------------------------------------------------------------------------------------ C2 hot loop
 class C2Loop:
     """The per-step work of pipeline_FaithDiff_tlc.py:1324-1409 for one 128^2 tile (C2), on the pipeline's own
@@ -278,11 +305,15 @@ class C2Loop:
         s_, sn = self.sig[i % 20], self.sig[i % 20 + 1]
         ops.tlc_scale_input(self.canvas, self.rows, self.cols, h, h, k, k, 0, self.grid.ntiles, self.cfg, s_,
                             self.xin, t_out=self.t_buf, timestep=self.ts[i % 20])
-        eps = self.unet.run(*self.args(), cond_embedded=True)
+        self.eps = eps = self.unet.run(*self.args(), cond_embedded=True)
         ops.tlc_cfg_euler_step(eps, self.canvas, self.rows, self.cols, h, h, k, k, 0, self.grid.ntiles, self.cfg,
                                5.0, 0.0, s_, sn, self.out_tiles)
         ops.tlc_blend(self.out_tiles, self.weights, self.rows, self.cols, 4, h, h, k, k, self.nxt)
         self.canvas, self.nxt = self.nxt, self.canvas
+
+    def outputs(self):
+        """What the last step handed back: the UNet's noise prediction, the stepped tiles and the blended canvas."""
+        return {"eps": self.eps.clone(), "tiles": self.out_tiles.clone(), "canvas": self.canvas.clone()}
 
 
 # ------------------------------------------------------------------------------------------------ kernel families
@@ -409,6 +440,7 @@ def run_pipeline_image(pipe, img, H, W, steps, target, seed=42):
     torch.cuda.synchronize()
     el = time.perf_counter() - t0
     tm.finite = bool(torch.isfinite(last["lat"]).all().item()) if "lat" in last else None
+    tm.latents = last.get("lat")
     return el, tm
 
 
@@ -459,7 +491,7 @@ def pipeline_leg(pipe, size, steps=20):
             "pre_loop_ms": round(tm.span_ms("call_start", "loop_start"), 2), "latents_finite": tm.finite}
 
 
-def c3_run(pipe, world, rank, dev, size, steps, warm=True, tag="C3"):
+def c3_run(pipe, world, rank, dev, size, steps, warm=True, tag="C3", keep=None):
     """BASELINE configs[2]: one size^2 image (49 TLC tiles at 4096^2) restored by all ranks together (configs[3]
     at 8192^2, 225 tiles, with the use_fp8 model)."""
     from FaithDiff.pipelines.tlc import TileGrid
@@ -476,6 +508,8 @@ def c3_run(pipe, world, rank, dev, size, steps, warm=True, tag="C3"):
         barrier(world)
     finally:
         pipe.disable_vae_tiling()
+    if keep is not None:  # --dump-outputs: the final latents of the timed call
+        keep["latents"] = tm.latents
     s = max_over_ranks(s, world, dev)
     st = tm.step_ms()
     loop_s = max_over_ranks(sum(st) / 1e3, world, dev)
@@ -617,13 +651,14 @@ def main(argv=None):
                                        "broadcast_s": round(pipe.last_broadcast_s, 3),
                                        "backend": dist.get_backend()}
 
+    dumped = {}  # --dump-outputs: name -> tensor, what the timed path's last step / call returned
     if args.workload in ("c3", "c4"):
         size, tag = (args.c3_size, "C3") if args.workload == "c3" else (args.c4_size, "C4")
         c3_run(pipe, world, rank, dev, size, 1, warm=False, tag=tag)  # warm-up: graphs captured
         reps = []
         barrier(world)
         for _ in range(max(1, args.steps // 20)):
-            reps.append(c3_run(pipe, world, rank, dev, size, args.c3_steps, warm=False, tag=tag))
+            reps.append(c3_run(pipe, world, rank, dev, size, args.c3_steps, warm=False, tag=tag, keep=dumped))
         r = reps[-1]
         what = (f"C3 tile-steps/sec @{size}px 20-step ({r['ntiles']} TLC tiles, tile-sharded over RCCL)"
                 if tag == "C3" else f"C4 tile-steps/sec @{size}px output 20-step, fp8 UNet ({r['ntiles']} TLC "
@@ -644,6 +679,7 @@ def main(argv=None):
         barrier(world)
         t = max_over_ranks(time.perf_counter() - t0, world, dev)
         stds = check_batch(out, lat, len(imgs))
+        dumped["latents"] = lat
         st = tm.step_ms()
         result.update({"metric": "C5 images/sec, 1024px 50-step, batch of 8 split over ranks",
                        "value": round(args.c5_images / t, 4), "unit": "images/s", "scaling": "strong",
@@ -671,6 +707,8 @@ def main(argv=None):
         barrier(world)
         wall = time.perf_counter() - t0
         t_max = max_over_ranks(wall, world, dev)
+        if args.dump_outputs:
+            dumped.update(loop.outputs())
         for i in range(args.profile_steps):
             loop.step(i)
         torch.cuda.synchronize()
@@ -693,17 +731,19 @@ def main(argv=None):
             "step_roofline": {"bound": "mfma", "achieved": round(flops / step_s / 1e12, 1), "peak": PEAK_BF16_TFLOPS,
                               "unit": "TFLOP/s", "frac": round(flops / step_s / 1e12 / PEAK_BF16_TFLOPS, 4),
                               "algorithmic_flops_per_step": flops, "event_ms_per_step": round(step_s * 1e3, 3)}})
-        if not args.no_roofline:
+        if args.full and not args.no_roofline:
             rl, _ = roofline_leg(loop, args.fp8)
             result.update(rl)
-        if not args.no_vae:
+        if args.full and not args.no_vae:
             result.update(vae_leg(pipe, loop))
         del loop
-        if not args.no_pipeline:
+        if args.full and not args.no_pipeline:
             result["pipeline"] = pipeline_leg(pipe, args.size)
-        if not args.no_c3:
+        if args.full and not args.no_c3:
             result["c3"] = c3_run(pipe, world, rank, dev, args.c3_size, args.c3_steps)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.dump_outputs and (rank == 0 or args.workload in ("c2", "c5")):  # c3 / c4: every rank holds the same canvas
+        dump_outputs(args.dump_outputs, {k: v for k, v in dumped.items() if v is not None}, rank)
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         try:
             result["cpu_baseline"] = cpu_baseline(args.size)
         except Exception as e:  # the baseline must not sink the GPU measurement

@@ -6,7 +6,7 @@
 #     smoke                     __graft_entry__.smoke()
 #     tests[=<pytest -k expr>]  the -m gpu suite (-v), parity metrics to gpurun_out/<tag>_parity_metrics.json
 #     tfile=<path>[:<-k expr>]  one GPU test file
-#     bench[=<args>]            bench.py line (args with ',' for spaces, e.g. bench=--fp8,--no-c3)
+#     bench[=<args>]            bench.py --full line (args with ',' for spaces, e.g. bench=--fp8,--no-c3)
 #     trace                     rocprofv3 kernel trace of the C2 bench: step window, GEMM instances, roofline check
 #     pmc=<unet|unet_fp8|vae|attn>   counter passes (scripts/prof.sh)
 #     probe=<script>[,args]     a python probe / measurement script
@@ -35,9 +35,9 @@ for ph in "$@"; do
       rc=$?; tail -8 $out.log ;;
     bench)
       [ -n "$arg" ] && out=${out}_$(echo "$arg" | tr -c 'a-zA-Z0-9' '_' | sed 's/_*$//')
-      timeout -k 10 600 python bench.py ${arg//,/ } > $out.json 2> $out.err; rc=$?; tail -c 700 $out.json ;;
+      timeout -k 10 600 python bench.py --full ${arg//,/ } > $out.json 2> $out.err; rc=$?; tail -c 700 $out.json ;;
     trace)
-      bash scripts/trace.sh $TAG > $out.log 2>&1; rc=$?; tail -30 $out.log ;;
+      FD_OUT=$PWD/$(dirname $out) bash scripts/trace.sh $TAG > $out.log 2>&1; rc=$?; tail -30 $out.log ;;
     pmc)
       bash scripts/prof.sh $arg ${TAG}_${arg}_pmc > $out.log 2>&1; rc=$?; tail -3 $out.log ;;
     probe)
@@ -48,7 +48,7 @@ for ph in "$@"; do
       if [ $name = abv ]; then VA=""; else VA="--no-vae"; fi
       if [ $name = abf ]; then VA="$VA --fp8"; fi
       for r in $(seq $reps); do for e in "${arms[@]}"; do
-        env $e timeout -k 10 300 python bench.py --no-cpu-baseline $VA --no-c3 --no-pipeline --steps 30 > $out.run 2>&1 || { rc=$?; break 2; }
+        env $e timeout -k 10 300 python bench.py --full --no-cpu-baseline $VA --no-c3 --no-pipeline --steps 30 > $out.run 2>&1 || { rc=$?; break 2; }
         echo "$e $(tail -1 $out.run | python -c 'import json,sys; d=json.loads(sys.stdin.read()); print(d["ms_per_step"], d.get("roofline", {}).get("frac"), d.get("vae_decode_ms"))')" | tee -a $out.txt
         rc=0
       done; done ;;

@@ -51,6 +51,31 @@ def test_workloads_parse():
     assert a.workload == "c3" and a.c3_steps == 4
 
 
+def test_plain_run_is_lean_by_default():
+    """The extra legs (roofline, VAE, pipe(...), C3, CPU baseline) run only with --full."""
+    a = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert a.full is False and a.dump_outputs is None and a.steps == 7 and a.warmup == 2
+    a = bench.parse(["--full", "--no-c3", "--dump-outputs", "out"])
+    assert a.full is True and a.no_c3 is True and a.dump_outputs == "out"
+
+
+def test_dump_outputs_writes_float32_npy_within_budget(tmp_path, monkeypatch):
+    """--dump-outputs: one float32 .npy per array; an array over its share of the budget is written as the same seeded
+    sample on every call, so two runs can be compared element for element."""
+    import numpy as np
+    import torch
+    small = torch.arange(24, dtype=torch.bfloat16).reshape(2, 3, 4)
+    big = torch.arange(5000, dtype=torch.float64)
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 2 * 4 * 1000)  # 1000 float32 elements per array
+    bench.dump_outputs(str(tmp_path / "a"), {"small": small, "big": big})
+    bench.dump_outputs(str(tmp_path / "b"), {"small": small, "big": big}, rank=1)
+    s, b = np.load(tmp_path / "a" / "small.npy"), np.load(tmp_path / "a" / "big.npy")
+    assert s.dtype == np.float32 and s.shape == (2, 3, 4) and np.array_equal(s, small.float().numpy())
+    assert b.dtype == np.float32 and b.shape == (1000,) and len(set(b.tolist())) == 1000
+    assert s.nbytes + b.nbytes <= 2 * 4 * 1000
+    assert np.array_equal(b, np.load(tmp_path / "b" / "big_rank1.npy"))
+
+
 def test_traffic_files_are_matched_by_workload(tmp_path, monkeypatch):
     """bench.load_traffic takes the newest committed PMC traffic file whose workload key matches (bf16 and the
     use_fp8 leg have their own keys), and returns None when no pass covers the workload."""
